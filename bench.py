@@ -8,6 +8,7 @@ SMPL-X + virtual measurements) on synthetic 224x224 crops, batch 64 per GPU, flo
     python bench.py --workload measurements --meshes 1000   # BASELINE configs[3]
     python bench.py --workload smplx --batch 64             # SMPL-X layer alone (LBS evidence)
     python bench.py --workload bvh --meshes 1000            # LBVH path of the intersection op
+    python bench.py --dump-outputs DIR                      # + the last timed step's outputs as DIR/*.npy
 
 One "step" of the default workload = one full forward of the regressor on one batch that is
 already resident in HBM (BASELINE.json configs[1]: "HRNet-W48 + SMPL-X head, random-init
@@ -377,6 +378,7 @@ def run_measurements(args, rank, world):
         barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    keep_outputs(args, {'measurements': out})
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=control_device())
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -451,6 +453,7 @@ def run_bvh(args, rank, world):
         ev1[i].record()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    keep_outputs(args, {'faces': f, 'bcs': b})
     ms = float(np.mean([a.elapsed_time(b_) for a, b_ in zip(ev0, ev1)]))
     overflow = int(mmi.mesh_to_mesh_forward.last_overflow.item())
     hits = int((f >= 0).sum().item())
@@ -530,6 +533,7 @@ def run_smplx(args, rank, world, net=None):
         ev1[i].record()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    keep_outputs(args, out)
     ms = float(np.mean([a.elapsed_time(b) for a, b in zip(ev0, ev1)]))
     nbytes = SMPLX_CONST_BYTES + SMPLX_BYTES_PER_BODY * B
     achieved = nbytes / (ms * 1e-3) / 1e9
@@ -547,6 +551,62 @@ def run_smplx(args, rank, world, net=None):
                      'bytes_per_launch_group': nbytes, 'ms_per_launch_group': ms,
                      'floor_us_at_6290': nbytes / 6290e9 * 1e6},
     }
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+LAST_OUTPUTS = {}          # --dump-outputs: name -> host array of the headline's last timed step
+
+
+def keep_outputs(args, obj):
+    """--dump-outputs: snapshot of the last timed step (the headline run only, not `also` records)."""
+    if getattr(args, 'dump_outputs', None) and not getattr(args, '_sub', False):
+        LAST_OUTPUTS.clear()
+        LAST_OUTPUTS.update(snapshot_outputs(obj))
+
+
+def snapshot_outputs(obj, prefix=''):
+    """Flattens what a caller of the timed path receives (nested dicts / lists / tuples of tensors,
+    KeypointTensor included) into {dotted name: host array}: floating point as float32 (float64 stays
+    float64), integers as float64 (exact below 2**53).  Non-array leaves are left out."""
+    import numpy as np
+    import torch
+    if hasattr(obj, '_t') and torch.is_tensor(obj._t):
+        obj = obj._t
+    if torch.is_tensor(obj):
+        obj = obj.detach().cpu()
+        obj = obj.float() if obj.is_floating_point() and obj.dtype != torch.float64 else obj
+        obj = obj.numpy()
+    if isinstance(obj, np.ndarray):
+        if obj.dtype == np.bool_ or np.issubdtype(obj.dtype, np.integer):
+            obj = obj.astype(np.float64)
+        elif obj.dtype != np.float64:
+            obj = obj.astype(np.float32)
+        return {prefix or 'output': np.ascontiguousarray(obj)}
+    items = (obj.items() if isinstance(obj, dict) else
+             enumerate(obj) if isinstance(obj, (list, tuple)) else ())
+    flat = {}
+    for k, v in items:
+        flat.update(snapshot_outputs(v, f'{prefix}.{k}' if prefix else str(k)))
+    return flat
+
+
+def write_outputs(arrays, folder, budget=DUMP_BUDGET_BYTES):
+    """Writes every array as <folder>/<name>.npy within `budget` bytes in all: arrays are taken
+    smallest first, each whole if it fits its share of what is left, else a fixed seeded sample of
+    its elements (flattened, ascending index order) that does."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    left = budget - 256 * len(arrays)                  # room for the .npy headers
+    order = sorted(arrays, key=lambda n: (arrays[n].nbytes, n))
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = left // (len(order) - i)
+        if a.nbytes > share:
+            k = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(osp.join(folder, name + '.npy'), a)
+        left -= a.nbytes
 
 
 def _compact(r):
@@ -677,8 +737,7 @@ def run_regressor(args, rank, world, local_rank):
     if stub:
         net = make_stub_network(args.size)
     else:
-        net, _ = ge.make_network(model_folder=f'/tmp/shapy_synth_models_r{local_rank}' if world > 1
-                                 else '/tmp/shapy_synth_models')
+        net, _ = ge.make_network()
         net.backbone.multi_stream = not args.single_stream
         net.backbone.compute_dtype = args.dtype
         if getattr(args, 'head_gemm', 'f32') == 'bf16x6':
@@ -755,6 +814,7 @@ def run_regressor(args, rank, world, local_rank):
     device_sync()
     dt = time.perf_counter() - t0
     h0.remove(); h1.remove()
+    keep_outputs(args, dict(out, gathered_betas=betas) if world > 1 else out)
     per_rank = None
     if world > 1:
         cdev = control_device()
@@ -1021,6 +1081,10 @@ def main():
     ap.add_argument('--no-also', action='store_true',
                     help='skip the `also` sub-records (the other BASELINE configurations, timed after '
                          'the headline\'s timed region in the default N = 1 run)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (the arrays its '
+                         'caller receives) as DIR/<name>.npy, float32 / float64, at most 64 MB in all '
+                         '(larger outputs: a fixed seeded sample); rank 0 only')
     args = ap.parse_args()
 
     STUB['on'] = bool(args.cpu_stub)
@@ -1075,6 +1139,8 @@ def main():
     if rank == 0:
         if finish is not None:
             res = finish(res)
+        if args.dump_outputs:
+            write_outputs(LAST_OUTPUTS, args.dump_outputs)
         # the JSON line is the LAST thing on stdout: whatever native libraries (RCCL prints its library
         # path through C stdio) still hold in their buffers goes out first
         sys.stdout.flush()

@@ -216,8 +216,8 @@ int shapy_hrnet_run(const ShapyOp *ops_host, int n_ops, const void *weights,
  * against its own stream with events. */
 int shapy_hrnet_lane_stream(int lane, void **stream_out);
 
-/* The same forward captured once into a hipGraph (side-stream branches included) and replayed
- * with one launch: removes the ~330 kernel launches + fork/join events per forward from the
+/* The same forward captured once into a hipGraph and replayed with one launch (captured on one
+ * stream: `multi_stream` is accepted and ignored, the replay equals the eager forward bit for bit): removes the ~330 kernel launches + fork/join events per forward from the
  * host, which dominate at small batch.  All pointers are baked into the graph: the caller
  * keeps input / workspace / features_out / weights alive and at the same addresses for the
  * life of the graph, copies new images into `input_nchw` before shapy_hrnet_graph_launch and

@@ -58,17 +58,22 @@ extern "C" int shapy_hrnet_graph_create(const ShapyOp *ops, int n_ops, const voi
   if (dtype != SHAPY_DTYPE_F32 && dtype != SHAPY_DTYPE_BF16 && dtype != SHAPY_DTYPE_F32X6)
     return SHAPY_EINVAL;
   if (cnt_per_image < 0 || (cnt_per_image > 0 && !counters)) return SHAPY_EINVAL;
+  // The graph is captured on ONE stream, whatever `multi_stream` asks: the first replay of a graph
+  // captured across the side lanes (fork / join events, parallel branches) crashes inside
+  // hipGraphLaunch with the HIP 7.0 runtime, while the same launches captured on one stream replay
+  // correctly -- and bit-identically to the eager forward on the lanes (same kernels, same buffers).
+  (void)multi_stream;
   hipStream_t cs = nullptr;
   SHAPY_HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
   // a plain (uncaptured) pass first: creates the side streams / events and validates the ops
   int rc = shapy::hrnet_run(ops, n_ops, weights, input_nchw, workspace, ws_elems_per_image, counters,
-                            cnt_per_image, features_out, B, H, W, multi_stream, dtype, cs);
+                            cnt_per_image, features_out, B, H, W, 0, dtype, cs);
   if (rc == 0) rc = (int)hipStreamSynchronize(cs);
   hipGraph_t graph = nullptr;
   if (rc == 0) rc = (int)hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
   if (rc == 0) {
     rc = shapy::hrnet_run(ops, n_ops, weights, input_nchw, workspace, ws_elems_per_image, counters,
-                          cnt_per_image, features_out, B, H, W, multi_stream, dtype, cs);
+                          cnt_per_image, features_out, B, H, W, 0, dtype, cs);
     const int rc2 = (int)hipStreamEndCapture(cs, &graph);
     if (rc == 0) rc = rc2;
   }

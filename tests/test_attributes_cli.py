@@ -56,9 +56,9 @@ def test_regressor_attributes_routing(tmp_path):
         p = Polynomial(10, 15)
         torch.save({'state_dict': {'b2a.' + k: v for k, v in p.state_dict().items()}},
                    tmp_path / f'{name}.ckpt')
-    syn.write_synthetic_smplx('/tmp/shapy_synth_models', 0)
+    syn.write_synthetic_smplx(str(tmp_path / 'models'), 0)
     cfg = merge_config([osp.join(ROOT, 'configs/b2a_expose_hrnet_demo.yaml')], [
-        'body_model.model_folder=/tmp/shapy_synth_models',
+        f'body_model.model_folder={tmp_path}/models',
         'network.smplx.backbone.hrnet.pretrained_path=', 'network.smplx.compute_measurements=False',
         f'network.smplx.b2a_males_checkpoint={tmp_path}/m.ckpt',
         f'network.smplx.b2a_females_checkpoint={tmp_path}/f.ckpt'])
@@ -86,7 +86,7 @@ def test_virtual_measurements_cli(tmp_path):
     import virtual_measurements as vm
     from oracle import body_np, measure
     from shapy_amd.utils import synthetic as syn
-    syn.write_synthetic_smplx('/tmp/shapy_synth_models', 0)
+    syn.write_synthetic_smplx(str(tmp_path / 'models'), 0)
     r = syn.rng_for(1, 'vm')
     (tmp_path / 'in').mkdir()
     betas = r.standard_normal(10).astype(np.float32)
@@ -94,7 +94,7 @@ def test_virtual_measurements_cli(tmp_path):
     data = osp.join(ROOT, 'shapy_amd', 'data')
     res = vm.main(str(tmp_path / 'in'), str(tmp_path / 'out'),
                   osp.join(data, 'measurement_defitions.yaml'),
-                  osp.join(data, 'smplx_measurements.yaml'), '/tmp/shapy_synth_models')
+                  osp.join(data, 'smplx_measurements.yaml'), str(tmp_path / 'models'))
     model = syn.make_synthetic_smplx(0)
     v = (model['v_template'][None] + body_np.blend_shapes(betas[None], model['shapedirs'][:, :, :10]))
     lm = measure.load_landmarks(osp.join(data, 'measurement_defitions.yaml'),

@@ -588,12 +588,12 @@ def ref_no_relu(x, w, b):
 
 # ------------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
-def network():
+def network(tmp_path_factory):
     _need_gpu()
     from shapy_amd.config import merge_config
     from shapy_amd.models import build_model
     from shapy_amd.utils import synthetic as syn
-    folder = '/tmp/shapy_synth_models'
+    folder = str(tmp_path_factory.mktemp('synth_models'))
     syn.write_synthetic_smplx(folder, 0)
     cfg = merge_config([osp.join(ROOT, 'configs/b2a_expose_hrnet_demo.yaml')], [
         f'body_model.model_folder={folder}',
@@ -800,7 +800,7 @@ def test_winograd_guard_calibration_and_wide_batchnorm_scales():
     from oracle import hrnet_torch
     from shapy_amd.utils import synthetic as syn
     from wino_guard_report import make_wild
-    net, _ = ge.make_network(model_folder='/tmp/shapy_synth_models_guard')
+    net, _ = ge.make_network()
     bb = net.backbone
     assert bb.wino_guard and bb.conv_algo == 'winograd4'
     x = torch.from_numpy(syn.synthetic_images(2, 224, 21)).cuda()
@@ -1717,7 +1717,9 @@ def test_hull_edge_cases_vs_oracle(network):
     assert abs(out5[1] - 1.8) < 1e-6
 
 
-def _nccl_worker(rank, world, port, q):
+def _nccl_worker(rank, world, port, q, backend='nccl'):
+    """backend 'nccl': one GPU per rank, the betas gathered by RCCL; 'gloo': the ranks share GPU 0
+    (RCCL refuses two ranks on one device) and gather the betas over gloo from host memory."""
     import os
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank),
                       WORLD_SIZE=str(world), LOCAL_RANK=str(rank), HSA_ENABLE_IPC_MODE_LEGACY='0')
@@ -1725,18 +1727,19 @@ def _nccl_worker(rank, world, port, q):
     import __graft_entry__ as ge
     from shapy_amd import parallel
     from shapy_amd.utils import synthetic as syn
-    torch.cuda.set_device(rank)
-    dist.init_process_group('nccl', init_method='env://')
+    torch.cuda.set_device(rank if backend == 'nccl' else 0)
+    dist.init_process_group(backend, init_method='env://')
     try:
-        net, _ = ge.make_network(model_folder=f'/tmp/shapy_synth_models_nccl{rank}')
+        net, _ = ge.make_network()
         xs = [torch.from_numpy(syn.synthetic_images(2, 64, 100 + r)).cuda() for r in range(world)]
         gat = parallel.BetasGatherer(world)
+        to = (lambda t: t) if backend == 'nccl' else (lambda t: t.cpu())
         with torch.no_grad():
             mine = net(xs[rank], None)['stage_02']['betas']
-            g1 = gat(mine)
-            g2 = gat(mine + 1)                  # second step: joins the first gather
+            g1 = gat(to(mine))
+            g2 = gat(to(mine + 1))              # second step: joins the first gather
             gat.wait()
-            others = torch.cat([net(x, None)['stage_02']['betas'] for x in xs])
+            others = to(torch.cat([net(x, None)['stage_02']['betas'] for x in xs]))
         torch.cuda.synchronize()
         ok = (torch.equal(g1, others) and torch.equal(g2, others + 1) and gat.deferred_waits == 1)
         q.put((rank, bool(ok)))
@@ -1799,11 +1802,13 @@ def test_rccl_forced_gather_one_rank_both_modes():
 
 
 def test_rccl_allgather_two_ranks():
-    """The N > 1 path on real RCCL: two ranks, one GPU each; every rank's gathered betas equal
-    what it computes itself for all shards (same weights, deterministic kernels)."""
+    """The N > 1 path: two ranks, each running the HIP network on its own shard; every rank's gathered
+    betas equal what it computes itself for all shards (same weights, deterministic kernels), the
+    second step joining the first gather.  With two GPUs: one GPU per rank, gathered by real RCCL.
+    With one GPU the two ranks share it and gather over gloo -- RCCL refuses two ranks on one device;
+    its collective on one rank is test_rccl_forced_gather_one_rank_both_modes."""
     _need_gpu()
-    if torch.cuda.device_count() < 2:
-        pytest.skip('needs 2 GPUs')
+    backend = 'nccl' if torch.cuda.device_count() >= 2 else 'gloo'
     import socket
     import torch.multiprocessing as mp
     with socket.socket() as s:
@@ -1811,7 +1816,7 @@ def test_rccl_allgather_two_ranks():
         port = s.getsockname()[1]
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    procs = [ctx.Process(target=_nccl_worker, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_nccl_worker, args=(r, 2, port, q, backend)) for r in range(2)]
     for p in procs:
         p.start()
     res = sorted(q.get(timeout=600) for _ in procs)

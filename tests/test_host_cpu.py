@@ -45,7 +45,7 @@ def test_cmd_parser():
 
 
 # ---- C-ABI --------------------------------------------------------------------------------
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol(tmp_path):
     import __graft_entry__ as ge
     ge.build()
     from shapy_amd import _lib
@@ -60,7 +60,7 @@ def test_library_exports_every_declared_symbol():
     # struct layouts agree with the C header (sizeof through a tiny C program)
     src = '#include <stdio.h>\n#include "shapy_hip.h"\nint main(){printf("%zu %zu %zu", ' \
           'sizeof(ShapyConv), sizeof(ShapyOp), sizeof(ShapySmplxModel));return 0;}'
-    exe = '/tmp/shapy_sizeof'
+    exe = str(tmp_path / 'shapy_sizeof')
     subprocess.run(['gcc', '-x', 'c', '-', '-I', osp.join(ROOT, 'include'), '-o', exe],
                    input=src.encode(), check=True)
     sizes = [int(x) for x in subprocess.check_output([exe]).split()]
@@ -748,7 +748,7 @@ def test_bf16_plan_keeps_the_48_channel_branch_unpadded():
     """bf16 rows are addressed in 8-channel (16-byte) slots; the 48-channel branch is NOT padded to
     64 channels any more (csrc/conv_igemm.hip: flat-K kernel for Cin % 32 != 0)."""
     import __graft_entry__ as ge
-    net, _ = ge.make_network(model_folder='/tmp/shapy_synth_models', device='cpu')
+    net, _ = ge.make_network(device='cpu')
     plan = net.backbone._build_plan(64, 64, bf16=True)
     convs = [o for o in plan.ops if o['type'] == 0]
     assert any(o['Cin'] == 48 and o['Cout'] == 48 and o['ksize'] == 3 for o in convs)
@@ -930,3 +930,54 @@ def test_w4g_schedule_native(tmp_path):
                            osp.join(root, 'tests', 'native', 'w4g_sched_test.cpp'), '-o', exe])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and 'W4G SCHEDULE OK' in r.stdout, r.stdout[-2000:]
+
+
+def test_bench_dump_outputs_flatten_and_budget(tmp_path):
+    """--dump-outputs: nested outputs flatten to float32 / float64 arrays by dotted name; within the
+    byte budget small arrays stay whole and a large one becomes the same seeded sample every time."""
+    import bench
+    from shapy_amd.models.body_models.utils import KeypointTensor
+    big = torch.arange(300_000, dtype=torch.float32).reshape(1000, 300)
+    out = {'stage_00': {'betas': torch.ones(2, 10, dtype=torch.bfloat16),
+                        'joints': KeypointTensor(torch.zeros(2, 5, 3))},
+           'stage_keys': ['stage_00'], 'faces': torch.arange(6).reshape(2, 3),
+           'f64': np.zeros(3), 'vertices': big, 'num_stages': 1}
+    flat = bench.snapshot_outputs(out)
+    assert sorted(flat) == ['f64', 'faces', 'stage_00.betas', 'stage_00.joints', 'vertices']
+    assert flat['stage_00.betas'].dtype == np.float32 and flat['faces'].dtype == np.float64
+    assert flat['stage_00.joints'].shape == (2, 5, 3) and flat['f64'].dtype == np.float64
+    budget = 400_000
+    for d in ('a', 'b'):
+        bench.write_outputs(flat, str(tmp_path / d), budget=budget)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(n + '.npy' for n in flat)
+    assert sum(osp.getsize(tmp_path / 'a' / f) for f in files) <= budget
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / 'a' / 'faces.npy'), np.arange(6.0).reshape(2, 3))
+    v = np.load(tmp_path / 'a' / 'vertices.npy')                   # sampled: values are their own indices
+    assert 0 < v.size < big.numel() and np.all(np.diff(v) > 0) and v[-1] < big.numel()
+
+
+def test_bench_dump_outputs_cli_with_stub_forward(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed step's arrays; same arguments, same files."""
+    import json
+    import subprocess
+    import sys
+    root = osp.dirname(osp.dirname(osp.abspath(__file__)))
+    dirs = []
+    for i in range(2):
+        d = tmp_path / f'run{i}'
+        r = subprocess.run([sys.executable, osp.join(root, 'bench.py'), '--gpus', '1', '--cpu-stub',
+                            '--steps', '4', '--warmup', '1', '--batch', '4', '--size', '32',
+                            '--dump-outputs', str(d)], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+        assert line['steps'] == 4 and line['ms_per_step'] > 0
+        dirs.append(d)
+    names = sorted(os.listdir(dirs[0]))
+    assert 'stage_02.betas.npy' in names and names == sorted(os.listdir(dirs[1]))
+    for n in names:
+        assert np.array_equal(np.load(dirs[0] / n), np.load(dirs[1] / n))
+    assert np.load(dirs[0] / 'stage_02.betas.npy').shape == (4, 10)

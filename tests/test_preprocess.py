@@ -85,14 +85,15 @@ def test_demo_entry_point_end_to_end(tmp_path):
     import __graft_entry__ as ge
     import demo
     from shapy_amd.utils.checkpointer import Checkpointer
-    net, _ = ge.make_network(seed=3)
+    models = str(tmp_path / 'models')
+    net, _ = ge.make_network(model_folder=models, seed=3)
     exp = tmp_path / 'exp'
     Checkpointer(net, save_dir=str(exp / 'checkpoints')).save_checkpoint('best_checkpoint')
     data = osp.join(root, 'shapy_amd', 'data')
     cfg, a = demo.parse([
         '--exp-cfg', osp.join(root, 'configs', 'b2a_expose_hrnet_demo.yaml'),
         '--output-folder', str(tmp_path / 'out'), '--save-params', 'true', '--save-mesh', 'true',
-        '--exp-opts', f'output_folder={exp}', 'body_model.model_folder=/tmp/shapy_synth_models',
+        '--exp-opts', f'output_folder={exp}', f'body_model.model_folder={models}',
         'network.smplx.backbone.hrnet.pretrained_path=',
         f'network.smplx.meas_definition_path={data}/measurement_defitions.yaml',
         f'network.smplx.meas_vertices_path={data}/smplx_measurements.yaml',
